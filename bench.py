@@ -19,13 +19,27 @@ with its code; under torch.distributed the ranks must equal --gpus and (RCCL) ea
 a device of its own, else the bench fails.  The N > 1 headline is the strong form: ONE batch of
 256 pairs LPT-sharded over the ranks, every step = execute + the device-side compact export
 (bg_batch_export_compact_async, no host wait) + the RCCL gather of the records to rank 0,
-pipelined, all inside the timed wall.  `weak` beside it: every rank aligns its own 256 pairs
+pipelined, all inside the timed wall.  `weak` beside it (--full): every rank aligns its own 256 pairs
 (the record gather after the timed region).  `--weak` makes the weak form the headline.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W]     the headline alone: set up, W warm-up
+                                   steps, K timed steps, the result line
+    python bench.py --full ...     the headline plus every other leg below
+    python bench.py --dump-outputs DIR ...   what the last timed step computed, as DIR/*.npy
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
     ... bench.py --config C4|C5    the whole 8-GPU job of SURVEY §8(d) C4 / C5, LPT-sharded over
                                    the ranks, export + RCCL gather to rank 0 inside every step
+
+A plain run measures what `value` needs and nothing else; `--full` adds the legs that take runs
+of their own (steady_state, affine, configs, host_to_host, cpu_baseline, and at N > 1 the other
+scaling form and rank 0's expansion of the gathered records), which are null in a plain line.
+
+`--dump-outputs DIR` writes, after the timed steps, the results of the last timed step as a caller
+of the hot path receives them from bg_batch_fetch (N > 1, strong form: rank 0's merged expansion
+of the gathered records), one float array per file: status, score, len (float64, one entry per
+pair in caller order), aligned1 and aligned2 (float32, the byte values of the pairs' aligned
+strings concatenated in caller order; beyond DUMP_MAX_ELEMS bytes a fixed seeded sample of
+positions).  The inputs are seeded, so two builds given the same arguments write comparable files.
 
 Fields beyond the driver's contract:
   roofline        the DP kernel (the dominant one) against §8(d)'s algorithmic bytes
@@ -33,14 +47,14 @@ Fields beyond the driver's contract:
                   HBM peak 8 TB/s; `bound` names the roof that binds (VALU issue) and `valu`
                   its fraction: PMC-measured VALU instructions x 64 lanes / kernel time against
                   256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6e12 lane-ops/s (MI355X_MICROARCH.md)
-  configs         (N = 1) the other BASELINE configurations on this GPU, each with its value,
+  configs         (--full, N = 1) the other BASELINE configurations on this GPU, each with its value,
                   step time, DP / traceback kernel times and roofline: C2, C3, and C4 / C5 as
                   one GPU's LPT share of their 8-GPU jobs
-  host_to_host    PCIe-inclusive rate through the streaming API (biogarden_amd.stream): residues
+  host_to_host    (--full) PCIe-inclusive rate through the streaming API (biogarden_amd.stream): residues
                   uploaded from host buffers, aligned strings downloaded to host buffers, four
                   handles in rotation so batches' uploads and downloads overlap the kernels of
                   the batches in flight (never `value`), with the host's time per phase
-  cpu_baseline    the oracle (oracle/refcpu.c: the reference's six full matrices, its loop order,
+  cpu_baseline    (--full) the oracle (oracle/refcpu.c: the reference's six full matrices, its loop order,
                   one reused aligner per thread) on this host's cores, plus a 1-core rate and C1
 """
 import argparse
@@ -64,11 +78,52 @@ VALU_CYC_PER_INSTR = 4.4                   # measured issue cost of the step's v
                                            # DPP mix (profiles/r01/micro_valu_rates.txt)
 MEASURED_ISSUE_LANE_OPS = 256 * 4 * 64 / VALU_CYC_PER_INSTR * 2.4e9
 SEED = workloads.SEED0 + 5                 # seed = 0xB10A11F0 + config index (M = 5)
+DUMP_MAX_ELEMS = 6 * 2 ** 20                # per aligned-string file: 24 MiB of float32, 48 MiB both
+DUMP_SEED = 0xD0B5
 METRIC = "GCUPS (billion DP cells/s), 10k×10k affine-gap semiglobal, 1/2/4/8 MI355X"
 
 
 def make_pairs(npairs, n1, n2, seed):
     return workloads.metric_pairs(npairs, n1, n2, seed)
+
+
+# ------------------------------------------------------------------ --dump-outputs
+
+
+def dump_outputs(path, status, score, strings1, strings2):
+    """DIR/<name>.npy of one batch's results in caller order: status, score, len (float64) and
+    the aligned strings' bytes, concatenated (float32; a fixed seeded sample of positions beyond
+    DUMP_MAX_ELEMS).  `strings1` / `strings2`: one uint8 array per pair."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "status.npy"), np.asarray(status, dtype=np.float64))
+    np.save(os.path.join(path, "score.npy"), np.asarray(score, dtype=np.float64))
+    np.save(os.path.join(path, "len.npy"), np.asarray([len(x) for x in strings1], dtype=np.float64))
+    for name, strings in (("aligned1", strings1), ("aligned2", strings2)):
+        flat = np.concatenate(strings) if len(strings) else np.zeros(0, dtype=np.uint8)
+        if flat.size > DUMP_MAX_ELEMS:
+            keep = np.random.default_rng(DUMP_SEED).choice(flat.size, DUMP_MAX_ELEMS, replace=False)
+            flat = flat[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), flat.astype(np.float32))
+
+
+def dump_fetched(path, h):
+    """The handle's last execute through bg_batch_fetch, written by dump_outputs."""
+    import numpy as np
+    res = h.fetch_raw()
+    o1 = np.frombuffer(res["out1"], dtype=np.uint8)
+    o2 = np.frombuffer(res["out2"], dtype=np.uint8)
+    spans = [(o, o + n) for o, n in zip(res["offset"], res["len"])]
+    dump_outputs(path, res["status"], res["score"], [o1[lo:hi] for lo, hi in spans],
+                 [o2[lo:hi] for lo, hi in spans])
+
+
+def dump_merged(path, merged):
+    """Rank 0's merged expansion of the gathered records (result dicts in caller order)."""
+    import numpy as np
+    dump_outputs(path, [r["status"] for r in merged], [r["score"] for r in merged],
+                 [np.frombuffer(r["aligned1"], dtype=np.uint8) for r in merged],
+                 [np.frombuffer(r["aligned2"], dtype=np.uint8) for r in merged])
 
 
 # ------------------------------------------------------------------ host description
@@ -556,8 +611,16 @@ def dry_line(args, world, rank, dist):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, every other leg: steady_state, affine, configs, "
+                         "host_to_host, cpu_baseline, at N > 1 the other scaling form and rank "
+                         "0's expansion of the gathered records (the --no-* / --configs / --cpu-* / "
+                         "--h2h-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed step's results to "
+                         "DIR/<name>.npy (status, score, len, aligned1, aligned2)")
     ap.add_argument("--pairs", type=int, default=256)
     ap.add_argument("--len1", type=int, default=10000)
     ap.add_argument("--len2", type=int, default=10000)
@@ -603,6 +666,11 @@ def main():
                     help="--group members as device ids (a device may repeat: virtual shards), "
                          "default 0..N-1")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.dry_run or args.group or args.config):
+        ap.error("--dump-outputs covers the metric workload (not --dry-run, --group or --config)")
+    full = args.full
 
     # N ranks: one process per GPU.  Outside torch.distributed, --gpus N > 1 starts the N ranks
     # as a child (before anything here touches a GPU) and exits with its code; inside it, the
@@ -732,6 +800,7 @@ def main():
         if g is not None and rank == 0:
             recs = g.records()
             heads0 = [_native.compact_headers(b) for b in recs]
+        if g is not None and rank == 0 and (full or args.dump_outputs):
             # rank 0 expands the last step's gathered records into aligned strings (it holds the
             # inputs): the merged batch must be complete, in caller order, every status 0
             batch = make_pairs(args.pairs, args.len1, args.len2, SEED)
@@ -743,16 +812,22 @@ def main():
                             "expand_ms": round((time.perf_counter() - te) * 1e3, 2),
                             "covers": "rank 0, bg_compact_expand of the last step's gathered "
                                       "records (after the timed steps)"}
+            if args.dump_outputs:
+                dump_merged(args.dump_outputs, merged)
+        elif args.dump_outputs and rank == 0:
+            dump_fetched(args.dump_outputs, h)      # --no-gather: rank 0's own shard
     else:
         st, elapsed, dp_ms, fin_ms, total_cells = weak_leg(h)
         pairs = own
+        if args.dump_outputs and rank == 0:
+            dump_fetched(args.dump_outputs, h)
     cells = st["cells"]
     gcups = total_cells * args.steps / elapsed / 1e9
     ms_per_step = elapsed / args.steps * 1e3
     # not `value`: the same batch over 200 steps, where the first DP (no traceback beside it) and
     # the last traceback (nothing beside it) weigh 1/200 instead of 1/K
     steady = None
-    if not strong_head and not args.no_steady:
+    if full and not strong_head and not args.no_steady:
         ks = 200
         el_s, dp_s, fin_s = timed(h, ks, 2, barrier)
         el_s = max_over_ranks(el_s)
@@ -765,13 +840,13 @@ def main():
         roof["share"] = "rank 0's LPT share: %d of %d pairs" % (len(pairs), args.pairs)
 
     # ---- the other form beside the headline (N > 1)
-    if world > 1 and strong_head:
+    if full and world > 1 and strong_head:
         wst, wel, wdp, wfin, wtotal = weak_leg(h)
         weak = {"value": round(wtotal * args.steps / wel / 1e9, 3), "unit": "GCUPS",
                 "ms_per_step": round(wel / args.steps * 1e3, 4), "pairs_per_rank": len(own),
                 "dp_ms": round(wdp, 4), "finish_ms": round(wfin, 4), "scaling": "weak",
                 "gather_in_wall": False, "kernel": kernel_info(wst, args.pipeline)}
-    elif world > 1:
+    elif full and world > 1:
         hs = _native.Handle(local_rank)
         hs.set_pipeline(args.pipeline)
         sst, se, sdp, sfin, scells, _, spairs, _ = strong_leg(hs)
@@ -800,7 +875,7 @@ def main():
 
     # ---- MA: the same pairs with a genuinely affine gap model (open < extend)
     aff = None
-    if not args.no_affine:
+    if full and not args.no_affine:
         a2, b2 = args.affine_open, args.affine_extend
         h.prepare(args.mode, own, sc, a2, b2)
         sta = h.stats()
@@ -818,14 +893,14 @@ def main():
 
     # ---- the other BASELINE configurations on this GPU (N = 1)
     cfgs = None
-    if world == 1 and args.configs:
+    if full and world == 1 and args.configs:
         cfgs = {}
         for name in [c for c in args.configs.split(",") if c]:
             cfgs[name] = config_leg(h, sc, name, barrier, args.pipeline)
 
     # ---- host-to-host rate (not `value`): host buffers in, aligned strings back on the host
     h2h = None
-    if not args.no_h2h:
+    if full and not args.no_h2h:
         queues = int(os.environ.get("GPU_MAX_HW_QUEUES") or 4)
         h2h = host_to_host(own, args.mode, args.open, args.extend, local_rank,
                            handles=args.h2h_handles, rounds=args.h2h_rounds,
@@ -846,7 +921,7 @@ def main():
 
     # ---- CPU baseline: the oracle on a bounded sample of the same workload (rank 0, N = 1)
     cpu = None
-    if not args.no_cpu and world == 1:
+    if full and not args.no_cpu and world == 1:
         cpu = cpu_section(own, gpu_scores, args.mode, args.open, args.extend, host_info(),
                           args.cpu_pairs, args.cpu_one_pairs)
 
@@ -861,6 +936,7 @@ def main():
         "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True,
         "scaling": "strong" if strong_head else "weak",
+        "full": full,
         "vs_baseline": None,
         "dtype": "int32",
         "data": "synthetic (uniform DNA, numpy PCG64 seed 0x%X%s)" % (

@@ -1,5 +1,5 @@
 # Profiles of the current build, as the bench runs it (pipeline depth 3):
-#  1. rocprofv3 --kernel-trace --stats of the default bench (M, MA and the C2-C5 legs);
+#  1. rocprofv3 --kernel-trace --stats of the full bench (M, MA and the C2-C5 legs);
 #  2. PMC passes (one counter group per pass, kernel trace only) for M, MA, C2, C3, C4, C5, each
 #     summarised into profiles/pmc_<workload>.json by tools/pmc_traffic.py.
 # Stops at the first failing GPU step.   TAG=r03 bash tools/prof_all.sh
@@ -7,7 +7,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 TAG=${TAG:-run}; OUT=gpurun_out/prof_$TAG; mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- \
-  python3 bench.py --no-cpu --no-h2h --steps 20 --warmup 5 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err \
+  python3 bench.py --full --no-cpu --no-h2h --steps 20 --warmup 5 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err \
   || { tail -5 $OUT/stats.err; exit 1; }
 echo "stats ok"
 G1="SQ_WAVES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_LDS GRBM_GUI_ACTIVE"

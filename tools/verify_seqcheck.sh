@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/seq; export TMPDIR=/tmp
 cp biogarden_amd/libbiogarden_gpu.so /tmp/lib_tree.so
 cp exp/seqdbg.so biogarden_amd/libbiogarden_gpu.so
 O=gpurun_out/seq
-timeout -k 10 200 python bench.py --no-cpu --no-h2h --configs C3 > $O/bench.out 2> $O/bench.err; r1=$?
+timeout -k 10 200 python bench.py --full --no-cpu --no-h2h --configs C3 > $O/bench.out 2> $O/bench.err; r1=$?
 timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_wide.py -q -s -m gpu --timeout 200 --timeout-method thread > $O/tests.out 2>&1; r2=$?
 cp /tmp/lib_tree.so biogarden_amd/libbiogarden_gpu.so
 echo "bench rc=$r1 tests rc=$r2 $(tail -1 $O/tests.out)"
