@@ -30,7 +30,8 @@ EXPORTS = ["bg_scoring_builtin", "bg_aligner_new", "bg_aligner_free", "bg_align"
            "bg_group_member", "bg_group_align_batch", "bg_group_plan", "bg_group_buffer_size",
            "bg_group_timing", "bg_group_submit", "bg_group_collect", "bg_group_pending",
            "bg_get_stats_sized", "bg_batch_export_compact_bound", "bg_batch_export_compact_async",
-           "bg_set_option", "bg_get_option", "bg_wait_diag"]
+           "bg_set_option", "bg_get_option", "bg_wait_diag", "bg_hamming_batch",
+           "bg_mismatch_matrix", "bg_dist_last_ms"]
 
 # bg_set_option keys (include/biogarden_gpu.h BG_OPT_*), by their BG_OPTIONS names
 OPTIONS = ("grouped", "group_pairs", "group_waves", "wide_waves", "fin_waves", "fin_slots",
@@ -169,6 +170,14 @@ def lib():
     L.bg_edit_distance_batch.argtypes = pair_args + [ctypes.POINTER(ctypes.c_uint64)]
     L.bg_lcs_batch.argtypes = pair_args + [c_u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64)]
+    L.bg_hamming_batch.argtypes = pair_args + [ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.POINTER(ctypes.c_int32)]
+    L.bg_mismatch_matrix.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p),
+                                     ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t),
+                                     ctypes.c_void_p]
+    L.bg_dist_last_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     L.bg_group_new.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     L.bg_group_new.restype = ctypes.c_void_p
     L.bg_group_free.argtypes = [ctypes.c_void_p]
@@ -451,6 +460,49 @@ class Handle:
         check(lib().bg_lcs_batch(self._p, n, a1, n1, a2, n2, buf, cap, off, ln))
         raw = bytes(buf)
         return [raw[off[p]:off[p] + ln[p]] for p in range(n)]
+
+    def hamming_batch(self, pairs, transitions=True):
+        """bg_hamming_batch over pairs [(s1, s2)] -> (mismatches, transitions, status), three
+        lists; status 2 (InvalidInputSize) marks a pair of unequal lengths, whose counts are 0.
+        transitions=False skips that count (None is returned for it)."""
+        a1, n1, a2, n2, _ = self._arrays(pairs)
+        n = len(pairs)
+        mis = (ctypes.c_uint64 * max(n, 1))()
+        ts = (ctypes.c_uint64 * max(n, 1))() if transitions else None
+        st = (ctypes.c_int32 * max(n, 1))()
+        check(lib().bg_hamming_batch(self._p, n, a1, n1, a2, n2, mis, ts, st))
+        return list(mis[:n]), (list(ts[:n]) if transitions else None), list(st[:n])
+
+    @staticmethod
+    def _rows(rows):
+        rows = [bytes(r) for r in rows]
+        n = len(rows)
+        return (ctypes.c_char_p * max(n, 1))(*rows), (ctypes.c_size_t * max(n, 1))(*[len(r) for r in rows]), rows
+
+    def mismatch_matrix(self, rows_a, rows_b=None):
+        """bg_mismatch_matrix -> numpy uint32 array: [i][j] = bytes of rows_a[i] and rows_b[j]
+        that differ, over the shorter of the two.  rows_b None: rows_a against itself (symmetric,
+        zero diagonal)."""
+        import numpy as np
+        pa, la, ka = self._rows(rows_a)
+        na = len(ka)
+        if rows_b is None:
+            out = np.zeros((na, na), dtype=np.uint32)
+            if na:
+                check(lib().bg_mismatch_matrix(self._p, na, pa, la, 0, None, None, out.ctypes.data))
+            return out
+        pb, lb, kb = self._rows(rows_b)
+        nb = len(kb)
+        out = np.zeros((na, nb), dtype=np.uint32)
+        if na and nb:
+            check(lib().bg_mismatch_matrix(self._p, na, pa, la, nb, pb, lb, out.ctypes.data))
+        return out
+
+    def dist_last_ms(self):
+        """Kernel ms of the last hamming_batch / mismatch_matrix (bg_dist_last_ms)."""
+        ms = ctypes.c_float()
+        check(lib().bg_dist_last_ms(self._p, ctypes.byref(ms)))
+        return ms.value
 
     def buffer_size(self):
         """The reference aligner's scratch dims this handle models (aligner.rs:30)."""

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "bg_device.h"
+#include "bg_dist.h"
 #include "bg_host_passes.h"
 #include "biogarden_gpu.h"
 
@@ -70,6 +71,9 @@ extern "C" void* bg_code_kernel_ptr();
 extern "C" void* bg_download_kernel_ptr();
 extern "C" void* bg_global_score_kernel_ptr();
 extern "C" void* bg_dp_aff_kernel_ptr(int R, int local);
+extern "C" void* bg_dist_pairs_kernel_ptr(int transitions);
+extern "C" void* bg_dist_rowpairs_kernel_ptr(void);
+extern "C" void* bg_dist_tile_kernel_ptr(void);
 extern "C" int bg_dp_aff_head_bytes(void);
 extern "C" int bg_dp_aff_wave_lds_bytes(int R, int K);
 extern "C" void* bg_finish_ack_kernel_ptr(int R, int mode);
@@ -337,6 +341,13 @@ struct bg_aligner {
   float dp_ms = 0.f, fin_ms = 0.f;
   hipEvent_t last[4] = {nullptr, nullptr, nullptr, nullptr};
 
+  // bg_hamming_batch / bg_mismatch_matrix (bg_dist.hip): buffers of their own, so a prepared
+  // batch stays as it was; the events time the last call's kernel (bg_dist_last_ms)
+  DevBuf distIn, distOut;
+  PinBuf distUp, distDown;
+  hipEvent_t distEv[2] = {nullptr, nullptr};
+  float distMs = 0.f;
+
   std::vector<BgResult> hres;
   PinBuf ho1, ho2;                 // fetch: the slot's aligned strings, downloaded
   PinBuf hresPin;                  // asynchronous fetch: the results, downloaded
@@ -357,7 +368,7 @@ struct bg_aligner {
 
   size_t device_bytes() const {
     size_t t = seq1.cap + seq2.cap + codes1.cap + codes2.cap + lut.cap + prof.cap + pairs.cap + recs.cap +
-               profScratch.cap;
+               profScratch.cap + distIn.cap + distOut.cap;
     for (const Slot& S : slot)
       t += S.trace.cap + S.bndM.cap + S.bndX.cap + S.aux.cap + S.out1.cap + S.out2.cap + S.results.cap +
            S.ops.cap + S.gran.cap + S.split.cap + S.gprog.cap;
@@ -506,7 +517,11 @@ extern "C" void bg_aligner_free(bg_aligner* h) {
   for (DevBuf* d : {&h->seq1, &h->seq2, &h->codes1, &h->codes2, &h->lut, &h->prof, &h->pairs, &h->recs,
                     &h->wgmapBuf, &h->gprogBuf, &h->dbgBuf, &h->dpDbg, &h->profScratch, &h->compactSizes})
     d->release();
-  for (PinBuf* q : {&h->ho1, &h->ho2, &h->up, &h->hresPin}) q->release();
+  for (PinBuf* q : {&h->ho1, &h->ho2, &h->up, &h->hresPin, &h->distUp, &h->distDown}) q->release();
+  h->distIn.release();
+  h->distOut.release();
+  for (auto& e : h->distEv)
+    if (e) (void)hipEventDestroy(e);
   for (Slot& S : h->slot) {
     for (DevBuf* d : {&S.trace, &S.bndM, &S.bndX, &S.aux, &S.out1, &S.out2, &S.results, &S.ops, &S.gran, &S.split,
                       &S.gprog, &S.keys, &S.xcnt})
@@ -2675,5 +2690,228 @@ extern "C" int bg_lcs_batch(bg_aligner* h, size_t npairs, const uint8_t* const* 
       if (ops[base + x] == 0) out[o++] = a1[base + x];       // diagonal column = a match
     len[p] = o - offset[p];
   }
+  return BG_OK;
+}
+
+// ---- Distances between equal-length rows (bg_dist.hip): analysis::seq::hamming_distance
+// (src/analysis/seq.rs:74-83), transition_transversion_ratio (:152-174) and the counts behind
+// analysis::stat::p_distance_matrix (src/analysis/stat.rs:138-152).  No DP and no batch: the calls
+// stage their input in buffers of their own, queue an upload, the kernel and a download on the
+// handle's DP stream behind whatever is queued there, and wait for that stream.
+namespace {
+
+constexpr size_t kDistMaxLen = ((size_t)1 << 30) - 1;
+
+// Queues [upload of up bytes] [zeroing of zero bytes of distOut] [launch] [download of down bytes]
+// on the DP stream, then waits for the download.  Two events around the zeroing and the launch
+// time the kernel (bg_dist_last_ms).  BG_DIST_REPEAT=n (tools/dist_bench.py) queues the zeroing and
+// the launch n times between the events, for a timed window longer than one short kernel; the
+// result is the last launch's and the time the average.
+template <class Launch>
+int dist_run(bg_aligner* h, size_t upBytes, size_t zeroBytes, size_t downBytes, Launch&& launch) {
+  for (auto& e : h->distEv)
+    if (!e) BG_HIP(hipEventCreate(&e));
+  const char* env = std::getenv("BG_DIST_REPEAT");
+  const int reps = env ? std::max(1, std::min(std::atoi(env), 100000)) : 1;
+  hipStream_t st = h->stream;
+  if (upBytes) BG_HIP(hipMemcpyAsync(h->distIn.p, h->distUp.p, upBytes, hipMemcpyHostToDevice, st));
+  BG_HIP(hipEventRecord(h->distEv[0], st));
+  for (int r = 0; r < reps; ++r) {
+    if (zeroBytes) BG_HIP(hipMemsetAsync(h->distOut.p, 0, zeroBytes, st));
+    const int rc = launch(st);
+    if (rc) return rc;
+  }
+  BG_HIP(hipGetLastError());
+  BG_HIP(hipEventRecord(h->distEv[1], st));
+  if (downBytes) BG_HIP(hipMemcpyAsync(h->distDown.p, h->distOut.p, downBytes, hipMemcpyDeviceToHost, st));
+  BG_HIP(hipStreamSynchronize(st));
+  BG_HIP(hipEventElapsedTime(&h->distMs, h->distEv[0], h->distEv[1]));
+  h->distMs /= (float)reps;
+  return BG_OK;
+}
+
+// Entry (i, j) over min(alen[i], blen[j]) bytes through the pair kernel: rows of different lengths
+// (the reference's zip, stat.rs:145), and the route the tiled kernel is measured against.
+int dist_matrix_rows(bg_aligner* h, size_t na, const uint8_t* const* a, const size_t* alen, size_t nb,
+                     const uint8_t* const* b, const size_t* blen, bool same, uint32_t* counts) {
+  const size_t nrows = same ? na : na + nb;
+  size_t bytes = 0, longest = 0;
+  for (size_t i = 0; i < na; ++i) { bytes += alen[i]; longest = std::max(longest, alen[i]); }
+  if (!same)
+    for (size_t j = 0; j < nb; ++j) { bytes += blen[j]; longest = std::max(longest, blen[j]); }
+  const size_t segs = std::max<size_t>(1, (longest + BG_DIST_SEG - 1) / BG_DIST_SEG);
+  if (segs * nb > 0x7fffffffu) return BG_E_ARG;        // one grid row per matrix row
+  // staging: [row offsets u64 x nrows][row lengths u32 x nrows][rows back to back]
+  const size_t offAt = 0, lenAt = round_up(nrows * 8, 16), rowAt = round_up(lenAt + nrows * 4, 256);
+  const size_t up = rowAt + bytes, out = na * nb * sizeof(uint32_t);
+  if (!h->distUp.ensure(up) || !h->distDown.ensure(out) || !h->distIn.ensure(up) || !h->distOut.ensure(out))
+    return BG_E_NOMEM;
+  uint8_t* U = h->distUp.as<uint8_t>();
+  uint64_t* off = reinterpret_cast<uint64_t*>(U + offAt);
+  uint32_t* len = reinterpret_cast<uint32_t*>(U + lenAt);
+  size_t at = rowAt;
+  for (size_t r = 0; r < nrows; ++r) {
+    const uint8_t* src = r < na ? a[r] : b[r - na];
+    const size_t n = r < na ? alen[r] : blen[r - na];
+    off[r] = at;
+    len[r] = (uint32_t)n;
+    if (n) std::memcpy(U + at, src, n);
+    at += n;
+  }
+  BgDistRowsArgs A;
+  const uint8_t* D = h->distIn.as<uint8_t>();
+  A.bytes = D;
+  A.aoff = reinterpret_cast<const uint64_t*>(D + offAt);
+  A.alen = reinterpret_cast<const uint32_t*>(D + lenAt);
+  A.boff = same ? A.aoff : A.aoff + na;
+  A.blen = same ? A.alen : A.alen + na;
+  A.counts = h->distOut.as<uint32_t>();
+  A.na = (uint32_t)na;
+  A.nb = (uint32_t)nb;
+  A.segs = (uint32_t)segs;
+  int rc = dist_run(h, up, out, out, [&](hipStream_t st) -> int {
+    for (size_t r0 = 0; r0 < na; r0 += 65535) {
+      A.row0 = (uint32_t)r0;
+      void* args[] = {&A};
+      BG_HIP(hipLaunchKernel(bg_dist_rowpairs_kernel_ptr(), dim3((unsigned)(segs * nb), (unsigned)std::min<size_t>(65535, na - r0)),
+                             dim3(BG_DIST_THREADS), args, 0, st));
+    }
+    return (int)BG_OK;
+  });
+  if (rc) return rc;
+  std::memcpy(counts, h->distDown.p, out);
+  return BG_OK;
+}
+
+}  // namespace
+
+extern "C" int bg_hamming_batch(bg_aligner* h, size_t npairs, const uint8_t* const* s1, const size_t* n1,
+                                const uint8_t* const* s2, const size_t* n2, uint64_t* mismatches,
+                                uint64_t* transitions, int32_t* status) {
+  if (!h || (npairs && (!s1 || !n1 || !s2 || !n2 || !mismatches || !status))) return BG_E_ARG;
+  size_t active = 0, bytes = 0, nseg = 0;
+  for (size_t p = 0; p < npairs; ++p) {
+    if (n1[p] > kDistMaxLen || n2[p] > kDistMaxLen || (n1[p] && !s1[p]) || (n2[p] && !s2[p])) return BG_E_ARG;
+    if (n1[p] != n2[p] || !n1[p]) continue;          // InvalidInputSize, or nothing to count
+    ++active;
+    bytes += 2 * n1[p];
+    nseg += (n1[p] + BG_DIST_SEG - 1) / BG_DIST_SEG;
+  }
+  if (nseg > 0x7fffffffu) return BG_E_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return BG_E_HIP;
+  h->distMs = 0.f;
+  // staging: [BgDistPair x active][segBase u32 x (active + 1)][s1 s2 of every pair, back to back]
+  const size_t baseAt = round_up(active * sizeof(BgDistPair), 16);
+  const size_t byteAt = round_up(baseAt + (active + 1) * 4, 256);
+  const size_t up = byteAt + bytes, out = active * 2 * sizeof(uint64_t);
+  if (active) {
+    if (!h->distUp.ensure(up) || !h->distDown.ensure(out) || !h->distIn.ensure(up) || !h->distOut.ensure(out))
+      return BG_E_NOMEM;
+    uint8_t* U = h->distUp.as<uint8_t>();
+    BgDistPair* P = reinterpret_cast<BgDistPair*>(U);
+    uint32_t* base = reinterpret_cast<uint32_t*>(U + baseAt);
+    size_t at = byteAt, q = 0, seg = 0;
+    for (size_t p = 0; p < npairs; ++p) {
+      const size_t n = n1[p];
+      if (n != n2[p] || !n) continue;
+      P[q] = BgDistPair{at, at + n, (uint32_t)n, 0u};
+      base[q++] = (uint32_t)seg;
+      seg += (n + BG_DIST_SEG - 1) / BG_DIST_SEG;
+      std::memcpy(U + at, s1[p], n);
+      std::memcpy(U + at + n, s2[p], n);
+      at += 2 * n;
+    }
+    base[q] = (uint32_t)seg;
+    BgDistPairsArgs A;
+    const uint8_t* D = h->distIn.as<uint8_t>();
+    A.bytes = D;
+    A.pairs = reinterpret_cast<const BgDistPair*>(D);
+    A.segBase = reinterpret_cast<const uint32_t*>(D + baseAt);
+    A.counts = h->distOut.as<unsigned long long>();
+    A.npairs = (uint32_t)active;
+    const int rc = dist_run(h, up, out, out, [&](hipStream_t st) -> int {
+      void* args[] = {&A};
+      BG_HIP(hipLaunchKernel(bg_dist_pairs_kernel_ptr(transitions != nullptr), dim3((unsigned)nseg),
+                             dim3(BG_DIST_THREADS), args, 0, st));
+      return (int)BG_OK;
+    });
+    if (rc) return rc;
+  }
+  const uint64_t* got = h->distDown.as<uint64_t>();
+  size_t q = 0;
+  for (size_t p = 0; p < npairs; ++p) {
+    const bool sized = n1[p] == n2[p];
+    status[p] = sized ? BG_OK : BG_INVALID_INPUT_SIZE;
+    const bool counted = sized && n1[p];
+    mismatches[p] = counted ? got[2 * q] : 0;
+    if (transitions) transitions[p] = counted ? got[2 * q + 1] : 0;
+    q += counted;
+  }
+  return BG_OK;
+}
+
+extern "C" int bg_mismatch_matrix(bg_aligner* h, size_t na, const uint8_t* const* a, const size_t* alen,
+                                  size_t nb, const uint8_t* const* b, const size_t* blen, uint32_t* counts) {
+  if (!h || (na && (!a || !alen))) return BG_E_ARG;
+  const bool same = !b && !nb;
+  if (!same && (!b || !blen || !nb)) return BG_E_ARG;
+  if (same) { b = a; blen = alen; nb = na; }
+  if (na && !counts) return BG_E_ARG;
+  bool uniform = true;
+  for (size_t i = 0; i < na; ++i) {
+    if (alen[i] > kDistMaxLen || (alen[i] && !a[i])) return BG_E_ARG;
+    uniform = uniform && alen[i] == alen[0];
+  }
+  for (size_t j = 0; j < nb && !same; ++j) {
+    if (blen[j] > kDistMaxLen || (blen[j] && !b[j])) return BG_E_ARG;
+    uniform = uniform && na && blen[j] == alen[0];
+  }
+  if (!na) return BG_OK;
+  // a matrix beyond 2^21 rows or columns (16 TiB of counts) cannot be allocated
+  if (na > ((size_t)1 << 21) || nb > ((size_t)1 << 21)) return BG_E_NOMEM;
+  if (hipSetDevice(h->device) != hipSuccess) return BG_E_HIP;
+  h->distMs = 0.f;
+  // BG_DIST_ROUTE=pairs: equal-length rows through the pair kernel too (tools/dist_bench.py's A/B)
+  const char* route = std::getenv("BG_DIST_ROUTE");
+  if (!uniform || (route && !std::strcmp(route, "pairs")))
+    return dist_matrix_rows(h, na, a, alen, nb, b, blen, same, counts);
+  const size_t L = alen[0], out = na * nb * sizeof(uint32_t);
+  if (!L) {                                          // no column: every count is 0
+    std::memset(counts, 0, out);
+    return BG_OK;
+  }
+  // staging: A's rows then B's at one stride, a multiple of 16 bytes, zero from L to the stride
+  const size_t stride = round_up(L, 16), nrows = same ? na : na + nb, up = nrows * stride;
+  if (!h->distUp.ensure(up) || !h->distDown.ensure(out) || !h->distIn.ensure(up) || !h->distOut.ensure(out))
+    return BG_E_NOMEM;
+  uint8_t* U = h->distUp.as<uint8_t>();
+  for (size_t r = 0; r < nrows; ++r) {
+    std::memcpy(U + r * stride, r < na ? a[r] : b[r - na], L);
+    std::memset(U + r * stride + L, 0, stride - L);
+  }
+  BgDistTileArgs A;
+  A.a = h->distIn.as<uint8_t>();
+  A.b = same ? A.a : A.a + na * stride;
+  A.counts = h->distOut.as<uint32_t>();
+  A.na = (uint32_t)na;
+  A.nb = (uint32_t)nb;
+  A.stride = (uint32_t)stride;
+  const size_t ta = (na + BG_DIST_TILE - 1) / BG_DIST_TILE, tb = (nb + BG_DIST_TILE - 1) / BG_DIST_TILE;
+  A.tilesB = (uint32_t)tb;
+  A.symmetric = same ? 1u : 0u;
+  const size_t tiles = same ? ta * (ta + 1) / 2 : ta * tb;      // <= 2^30 at 2^21 rows
+  const int rc = dist_run(h, up, 0, out, [&](hipStream_t st) -> int {
+    void* args[] = {&A};
+    BG_HIP(hipLaunchKernel(bg_dist_tile_kernel_ptr(), dim3((unsigned)tiles), dim3(BG_DIST_THREADS), args, 0, st));
+    return (int)BG_OK;
+  });
+  if (rc) return rc;
+  std::memcpy(counts, h->distDown.p, out);
+  return BG_OK;
+}
+
+extern "C" int bg_dist_last_ms(bg_aligner* h, float* kernel_ms) {
+  if (!h || !kernel_ms) return BG_E_ARG;
+  *kernel_ms = h->distMs;
   return BG_OK;
 }

@@ -7,6 +7,9 @@
 //   biogarden::ds::Tile                      src/ds/tile.rs:9-177
 //   biogarden::io::fasta::{Reader,Record}    src/io/fasta.rs:95-135, 205-272
 //   biogarden::BioError / Result             src/error.rs:8-14, 46
+//   biogarden::analysis::seq::{edit_distance, hamming_distance, transition_transversion_ratio}
+//                                            src/analysis/seq.rs:105-130, 74-83, 152-174
+//   biogarden::analysis::stat::p_distance_matrix   src/analysis/stat.rs:138-152
 //
 // Same method names, argument meaning and error behaviour: Err(InvalidArgumentRange) and
 // Err(InvalidInputSize) exactly where the reference returns them; ReferencePanic (an exception,
@@ -453,7 +456,57 @@ inline Result<size_t> edit_distance(const ds::Sequence& seq1, const ds::Sequence
   check(bg_edit_distance_batch(detail::Device::get(), 1, a.p1, a.n1, a.p2, a.n2, &d));
   return Result<size_t>((size_t)d);
 }
+// analysis::seq::hamming_distance (src/analysis/seq.rs:74-83): Err(InvalidInputSize) when the
+// lengths differ (:81)
+inline Result<size_t> hamming_distance(const ds::Sequence& seq1, const ds::Sequence& seq2) {
+  detail::PairArrays a(seq1, seq2);
+  uint64_t h = 0;
+  int32_t st = 0;
+  check(bg_hamming_batch(detail::Device::get(), 1, a.p1, a.n1, a.p2, a.n2, &h, nullptr, &st));
+  if (st == BG_INVALID_INPUT_SIZE) return BioError::InvalidInputSize;
+  return Result<size_t>((size_t)h);
+}
+// analysis::seq::transition_transversion_ratio (src/analysis/seq.rs:152-174): the GPU counts the
+// mismatches and, among them, the transitions (:164-170); the f64 division of :173 is done here
+// (inf when every mismatch is a transition, NaN without a mismatch, as in the reference)
+inline Result<double> transition_transversion_ratio(const ds::Sequence& seq1, const ds::Sequence& seq2) {
+  detail::PairArrays a(seq1, seq2);
+  uint64_t h = 0, t = 0;
+  int32_t st = 0;
+  check(bg_hamming_batch(detail::Device::get(), 1, a.p1, a.n1, a.p2, a.n2, &h, &t, &st));
+  if (st == BG_INVALID_INPUT_SIZE) return BioError::InvalidInputSize;
+  return Result<double>((double)t / ((double)h - (double)t));
+}
 }  // namespace seq
+
+namespace stat {
+// analysis::stat::p_distance_matrix (src/analysis/stat.rs:138-152).  The reference returns an
+// ndarray Array2<f32>; there is no ndarray to mirror here, so the matrix comes back row-major in
+// a vector with its dimension: at(i, j) = values[i * rows + j].  columns is the first row's
+// length (Tile::size, tile.rs); an empty tile throws ReferencePanic where the reference panics.
+struct DistanceMatrix {
+  size_t rows = 0;
+  std::vector<float> values;
+  float at(size_t i, size_t j) const { return values.at(i * rows + j); }
+};
+inline DistanceMatrix p_distance_matrix(const ds::Tile& matrix) {
+  if (matrix.is_empty()) throw ReferencePanic("index out of bounds: Tile::size of an empty tile");
+  const size_t n = matrix.len(), columns = matrix[0].len();
+  std::vector<const uint8_t*> p(n);
+  std::vector<size_t> len(n);
+  for (size_t i = 0; i < n; ++i) {
+    p[i] = matrix[i].chain.data();
+    len[i] = matrix[i].len();
+  }
+  std::vector<uint32_t> counts(n * n);
+  check(bg_mismatch_matrix(detail::Device::get(), n, p.data(), len.data(), 0, nullptr, nullptr, counts.data()));
+  DistanceMatrix d;
+  d.rows = n;
+  d.values.resize(n * n);
+  for (size_t k = 0; k < n * n; ++k) d.values[k] = (float)counts[k] / (float)columns;   // stat.rs:147
+  return d;
+}
+}  // namespace stat
 }  // namespace analysis
 
 namespace processing {

@@ -399,6 +399,35 @@ int bg_lcs_batch(bg_aligner* h, size_t npairs, const uint8_t* const* s1, const s
                  const uint8_t* const* s2, const size_t* n2, uint8_t* out, size_t out_cap,
                  uint64_t* offset, uint64_t* len);
 
+/* ---- Distances between equal-length rows (bg_dist.hip).  No DP: both calls use buffers of their
+ * own on the handle, queue on its DP stream behind whatever is queued there, wait, and leave a
+ * prepared batch exactly as it was (a later bg_batch_execute / bg_batch_fetch still works).
+ * Lengths above 2^30 - 1 or NULL arguments: BG_E_ARG. */
+
+/* analysis::seq::hamming_distance (src/analysis/seq.rs:74-83) and the two counts of
+ * transition_transversion_ratio (seq.rs:152-174) for a batch of pairs: mismatches[p] = bytes of
+ * pair p that differ, transitions[p] = those that are exactly (C,T), (T,C), (A,G) or (G,A)
+ * (:164-170; upper-case ASCII only).  status[p] = BG_OK, or BG_INVALID_INPUT_SIZE when
+ * n1[p] != n2[p] (both functions' Err(InvalidInputSize)): such a pair gets counts 0 and no device
+ * work.  transitions may be NULL (the count is then skipped).  The ratio itself is
+ * transitions / (mismatches - transitions) in f64 (seq.rs:173), left to the caller. */
+int bg_hamming_batch(bg_aligner* h, size_t npairs, const uint8_t* const* s1, const size_t* n1,
+                     const uint8_t* const* s2, const size_t* n2, uint64_t* mismatches,
+                     uint64_t* transitions, int32_t* status);
+
+/* The counts behind analysis::stat::p_distance_matrix (src/analysis/stat.rs:138-152): counts[i][j] =
+ * bytes of row a[i] and row b[j] that differ, over min(alen[i], blen[j]) bytes (zip, stat.rs:145).
+ * b == NULL && nb == 0: B is A; the result is na x na, symmetric, with a zero diagonal (:144).
+ * Rows of one length run on the tiled kernel; rows of different lengths go pair by pair through
+ * the kernel behind bg_hamming_batch.  p-distance = (f32)count / (f32)columns on the host. */
+int bg_mismatch_matrix(bg_aligner* h, size_t na, const uint8_t* const* a, const size_t* alen,
+                       size_t nb, const uint8_t* const* b, const size_t* blen,
+                       uint32_t* counts /* row-major na x (nb ? nb : na) */);
+
+/* Kernel time of this handle's last bg_hamming_batch / bg_mismatch_matrix in ms (HIP events on its
+ * stream around the kernel; 0 when the call needed no device work).  Not a reference interface. */
+int bg_dist_last_ms(bg_aligner* h, float* kernel_ms);
+
 /* ---- Streaming FASTA ingest (io::fasta::Reader::read / read_all, src/io/fasta.rs:95-135).
  * Records are returned in batches, residues back to back in one reader-owned buffer: record r
  * is seq[seq_off[r] .. seq_off[r+1]), its id the NUL-terminated text + id_off[r], its
